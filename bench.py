@@ -641,6 +641,38 @@ class _StdoutToStderr:
         return False
 
 
+DUMP_BYTES_MAX = 64 << 20
+DUMP_SKIP_FIELDS = ("reserved",)     # transient kernel state, not part of what the caller receives
+
+
+def dump_outputs(out_dir, res, blob, max_bytes=DUMP_BYTES_MAX, seed=0):
+    """--dump-outputs: the result records of one batch (one <field>.npy per field of abi.Result: float64, sr_align_quality float32)
+    and the byte strings they point to in the blob (consensus.npy, alleles.npy, alignment.npy: every junction's bytes, concatenated in
+    junction order, as float32; a kind of string no junction of the batch has -- the alignment rows when the caller did not ask for
+    them, as the timed path does not -- is not written).  The strings are cut out by the records' offsets and lengths, so bytes of
+    the blob no record points to are not compared.  A batch whose dump would exceed max_bytes is cut to a seeded sample of its junctions, the same for the same
+    batch; junction_index.npy says which."""
+    import numpy as np
+    names = [f for f in res.dtype.names if f not in DUMP_SKIP_FIELDS]
+    strings = (("consensus", "cons_off", "cons_len"), ("alleles", "allele_off", "allele_len"), ("alignment", "aln_off", "aln_len"))
+    per_junction = 8 * (len(names) + 1) + 4 * sum(res[ln].astype(np.int64) for _, _, ln in strings)
+    budget = max_bytes - 4096 * (len(names) + 4)      # (room for the .npy headers)
+    idx = np.arange(res.shape[0])
+    if int(per_junction.sum()) > budget:
+        order = np.random.default_rng(seed).permutation(res.shape[0])
+        keep = int(np.searchsorted(np.cumsum(per_junction[order]), budget, side="right"))
+        idx = np.sort(order[:keep])
+    sel = res[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "junction_index.npy"), idx.astype(np.float64))
+    for f in names:
+        np.save(os.path.join(out_dir, f + ".npy"), sel[f].astype(np.float32 if sel[f].dtype.kind == "f" else np.float64))
+    for name, off, ln in strings:
+        parts = [blob[int(o):int(o) + int(n)] for o, n in zip(sel[off], sel[ln]) if n > 0]
+        if parts:
+            np.save(os.path.join(out_dir, name + ".npy"), np.concatenate(parts).astype(np.float32))
+
+
 def _free_port():
     import socket
     with socket.socket() as so:
@@ -691,10 +723,15 @@ def main():
                          "overlapping step k) on ONE GPU with a one-rank communicator")
     ap.add_argument("--dump-rank0-view", default="", help="N > 1: rank 0 writes what it holds after the last step of each return path "
                                                           "(records + blob per path) to this .npz (tests compare it with the checker)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the last timed step computed (its own batch) as DIR/<name>.npy (e.g. bench_outputs/), float32 / float64, "
+                         "<= 64 MB in all (see dump_outputs); the inputs depend only on the arguments, so two builds compare output for output")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         _launch_ranks(args)        # (does not return)
     rank = int(os.environ.get("RANK", "0"))
@@ -930,6 +967,9 @@ def main():
             elif rank == 0 and args.dump_rank0_view:
                 nr, nb = gathered_n
                 rank0_view["rccl"] = (np.frombuffer(pinned[0].numpy()[:nr * rb_bytes].tobytes(), dtype=abi.result_dtype()), pinned[1].numpy()[:nb].copy())
+    if rank == 0 and args.dump_outputs:
+        # every timed region starts at step 0, so the last timed step ran rbs[(steps - 1) % len(rbs)]; nothing has run it since
+        dump_outputs(args.dump_outputs, *rbs[(k_step[0] - 1) % len(rbs)].fetch())
     # N > 1: `value` is the pipelined per-rank return (shm) when it was timed; the blocking gather is timed beside it (config.gather_*)
     first = ("shm" if "shm" in paths else paths[0]) if paths else None
     dt = region[first]["dt"]

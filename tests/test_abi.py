@@ -73,11 +73,11 @@ def test_compiled_cpp_caller_builds_and_fails_loudly_without_a_device():
     agree with the library, and without a usable GPU torali::msa() throws (no CPU path)."""
     import subprocess
     import torch
-    exe = os.path.join(ROOT, "tests", "cpp", "_build", "dropin_test")
+    exe = os.path.join(ROOT, "oracle", "_ref", "dropin_test")
     if not os.path.exists(exe):
         if not os.path.isdir("/root/reference/src"):
-            pytest.skip("tests/cpp/_build/dropin_test not built and /root/reference absent")
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "tests", "cpp")])
+            pytest.skip("oracle/_ref/dropin_test not built and the reference absent")
+        subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "dropin"])
     r = subprocess.run([exe, "abi"], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     if not torch.cuda.is_available():

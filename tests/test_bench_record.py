@@ -104,3 +104,34 @@ def test_traffic_stamp_follows_the_code_not_the_comments(tmp_path, monkeypatch):
     assert build.headline_kernel_hash() == here
     p.write_text(src + "\nnamespace dh { constexpr int dh_probe_of_the_stamp = 1; }\n")
     assert build.headline_kernel_hash() != here
+
+
+def test_dump_outputs_decodes_the_records_and_keeps_to_the_cap(tmp_path, port):
+    """--dump-outputs: one float .npy per record field plus the byte strings the records point to; over the cap, the same seeded
+    sample of junctions every time, and never more than the cap on disk."""
+    import numpy as np
+    from delly_amd import synth
+    b = synth.make_batch(40, mode="c2", seed=11)
+    res, blob = port.refine_batch(b)
+    full = tmp_path / "full"
+    bench.dump_outputs(str(full), res, blob)
+    got = {f[:-4]: np.load(str(full / f)) for f in os.listdir(str(full))}
+    assert all(a.dtype in (np.float32, np.float64) and a.size > 0 for a in got.values())
+    assert "reserved" not in got and got["junction_index"].tolist() == list(range(b.n))
+    assert got["ok"].tolist() == res["ok"].tolist() and got["sv_start"].tolist() == res["sv_start"].tolist()
+    want = b"".join(blob[int(o):int(o) + int(n)].tobytes() for o, n in zip(res["cons_off"], res["cons_len"]))
+    assert got["consensus"].astype(np.uint8).tobytes() == want and len(want) > 0
+    no_aln = res.copy()
+    no_aln["aln_len"] = 0           # the timed path asks for no alignment rows: no empty array stands in for them
+    bench.dump_outputs(str(tmp_path / "no_aln"), no_aln, blob)
+    written = os.listdir(str(tmp_path / "no_aln"))
+    assert "alignment.npy" not in written and "consensus.npy" in written and "alleles.npy" in written
+    cap = 40 * 1024 + 4096 * 40
+    cut1, cut2 = tmp_path / "cut1", tmp_path / "cut2"
+    bench.dump_outputs(str(cut1), res, blob, max_bytes=cap)
+    bench.dump_outputs(str(cut2), res, blob, max_bytes=cap)
+    assert sum(os.path.getsize(str(cut1 / f)) for f in os.listdir(str(cut1))) <= cap
+    idx = np.load(str(cut1 / "junction_index.npy"))
+    assert 0 < idx.size < b.n and idx.tolist() == np.load(str(cut2 / "junction_index.npy")).tolist()
+    for f in os.listdir(str(cut1)):
+        assert np.load(str(cut1 / f)).tobytes() == np.load(str(cut2 / f)).tobytes(), f

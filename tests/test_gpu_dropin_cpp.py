@@ -15,7 +15,7 @@ import pyoracle
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "tests", "cpp", "_build", "dropin_test")
+BIN = os.path.join(ROOT, "oracle", "_ref", "dropin_test")
 
 
 def _write_batch(path, b, params, realign, mode):
@@ -58,7 +58,7 @@ class _Reader:
 
 def _run(tmp_path, b, params, realign, mode):
     if not os.path.exists(BIN):
-        pytest.fail("tests/cpp/_build/dropin_test is not built (__graft_entry__.build() compiles it where /root/reference exists)")
+        pytest.fail("oracle/_ref/dropin_test is not built (__graft_entry__.build() compiles it where the reference exists)")
     inp, outp = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
     _write_batch(inp, b, params, realign, mode)
     r = subprocess.run([BIN, "run", inp, outp], capture_output=True, text=True, timeout=600)

@@ -17,7 +17,7 @@ from delly_amd import refine
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "tests", "cpp", "_build", "edlib_dropin_test")
+BIN = os.path.join(ROOT, "oracle", "_ref", "edlib_dropin_test")
 IUPAC = b"ACGT-MRWBSYDKEF"
 
 
@@ -113,7 +113,7 @@ def test_c_abi_full_result_vs_the_reference_edlib(gpu_ctx, reference):
 
 def test_compiled_caller_of_the_drop_in_edlib_h(tmp_path, reference):
     if not os.path.exists(BIN):
-        pytest.skip("tests/cpp/_build/edlib_dropin_test not built (needs /root/reference for the include path)")
+        pytest.skip("oracle/_ref/edlib_dropin_test not built (needs the reference for the include path)")
     extra = [(-1, 0, 0, 2, b"ACGT", b"ACGT")]          # an equality set the drop-in refuses: EDLIB_STATUS_ERROR, nothing allocated
     cases = CASES + extra
     fin, fout = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
