@@ -287,9 +287,15 @@ class Context:
         cap = n * (6000 if want_alignment else 3100) + int(blob.size) * (16 if want_alignment else 8) + 64
         out = np.zeros(cap, dtype=np.uint8)
         used = C.c_uint64(0)
-        rc = fn(self._ctx, n, _p(junc, C.c_void_p), _p(blob), _p(off, C.POINTER(C.c_uint64)),
-                C.c_uint64(off.size - 1), _p(res, C.c_void_p), _p(out), C.c_uint64(cap), C.byref(used),
-                int(bool(want_alignment)))
+        for _ in range(2):
+            rc = fn(self._ctx, n, _p(junc, C.c_void_p), _p(blob), _p(off, C.POINTER(C.c_uint64)),
+                    C.c_uint64(off.size - 1), _p(res, C.c_void_p), _p(out), C.c_uint64(out.size), C.byref(used),
+                    int(bool(want_alignment)))
+            if rc != abi.E_ARG or used.value <= out.size:
+                break
+            # the estimate is short where exact alleles span a long deletion (REF up to indelsize bases, src/split.h:606) and
+            # where alignment rows are that wide: the library returned the size needed, run once more into a blob of that size
+            out = np.zeros(int(used.value), dtype=np.uint8)
         self._check(rc)
         return res, out[:used.value]
 
@@ -606,8 +612,11 @@ class ResidentBatch:
         cap = self.n * 3100 + 8 * self._blob_bytes + 64
         out = np.zeros(cap, dtype=np.uint8)
         used = C.c_uint64(0)
-        self.ctx._check(self.ctx.lib.dellyhip_batch_fetch(self.ctx._ctx, self._b, _p(res, C.c_void_p), _p(out),
-                                                          C.c_uint64(cap), C.byref(used)))
+        rc = self.ctx.lib.dellyhip_batch_fetch(self.ctx._ctx, self._b, _p(res, C.c_void_p), _p(out), C.c_uint64(cap), C.byref(used))
+        if rc == abi.E_ARG and used.value > cap:   # (long alleles / alignment rows, as in Context._run_host: the size needed came back)
+            out = np.zeros(int(used.value), dtype=np.uint8)
+            rc = self.ctx.lib.dellyhip_batch_fetch(self.ctx._ctx, self._b, _p(res, C.c_void_p), _p(out), C.c_uint64(out.size), C.byref(used))
+        self.ctx._check(rc)
         return res, out[:used.value]
 
     def gather(self, comm, root=0, results_cap=None, blob_cap=None):

@@ -584,10 +584,12 @@ def tile_batch(batch, times):
     return Batch(chroms, junc, blob, off, batch.with_msa, truth)
 
 
-def make_big_deletions(shapes, seed=11, err=0.01, revcomp_every=0):
+def make_big_deletions(shapes, seed=11, err=0.01, revcomp_every=0, n_reads=0):
     """one DEL junction per (flank, ell): consensus = 2 * flank bases of the ALT haplotype with ONT-like errors -- BASELINE
     configs[3] as written is (5000, 700): a 10 kb consensus against a 20.7 kb reference window (longNeedle over 2 x 207 M cells;
-    the reference holds four int32 matrices of 830 MB for it, src/needle.h:52-103).  Use with abi.params_lr(realign=True)."""
+    the reference holds four int32 matrices of 830 MB for it, src/needle.h:52-103).  Use with abi.params_lr(realign=True).
+    n_reads > 0: that many long reads of the ALT haplotype per junction instead (msaEdlib first, with_msa = 2), each with up
+    to 100 bases cut from either end."""
     rng = np.random.default_rng(seed)
     W = 70000
     n = len(shapes)
@@ -597,16 +599,21 @@ def make_big_deletions(shapes, seed=11, err=0.01, revcomp_every=0):
     for k, (flank, ell) in enumerate(shapes):
         s0 = k * W + 20000
         hap = np.concatenate([chrom[s0 - flank:s0], chrom[s0 + ell:s0 + ell + flank]])
-        cons = _ont(rng, hap, err)
-        if revcomp_every and k % revcomp_every == 1:
-            cons = revcomp(cons)
+        junc[k]["seq_first"] = len(seqs)
+        if n_reads > 0:
+            for _ in range(n_reads):
+                seqs.append(_ont(rng, hap[int(rng.integers(0, 101)):hap.size - int(rng.integers(0, 101))], err))
+            junc[k]["n_seq"] = n_reads
+        else:
+            cons = _ont(rng, hap, err)
+            if revcomp_every and k % revcomp_every == 1:
+                cons = revcomp(cons)
+            seqs.append(cons)
+            junc[k]["n_seq"] = 1
         junc[k]["svid"] = k
         junc[k]["svt"] = 2
         junc[k]["sv_start"] = s0 + int(rng.integers(-3, 4))
         junc[k]["sv_end"] = s0 + ell + int(rng.integers(-3, 4))
-        junc[k]["seq_first"] = k
-        junc[k]["n_seq"] = 1
-        seqs.append(cons)
-    off = np.zeros(n + 1, dtype=np.uint64)
+    off = np.zeros(len(seqs) + 1, dtype=np.uint64)
     off[1:] = np.cumsum([x.size for x in seqs])
-    return Batch([chrom], junc, np.concatenate(seqs), off, 0, None)
+    return Batch([chrom], junc, np.concatenate(seqs), off, 2 if n_reads > 0 else 0, None)

@@ -77,3 +77,102 @@ PARAM_SETS = [None,
 def params_of(i):
     t = PARAM_SETS[i]
     return abi.Params(*t) if t else abi.params_sr()
+
+
+def _pack(chroms, junc, seqs, with_msa=0):
+    off = np.zeros(len(seqs) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([x.size for x in seqs])
+    return synth.Batch(chroms, junc, np.concatenate(seqs), off, with_msa, None)
+
+
+_SV_KINDS = ((2, "del"), (3, "dup"), (0, "inv0"), (1, "inv1"))
+
+
+def at_span(n, span, *, seed=1, lr=False, flank=None):
+    """DEL, DUP, INV 3to3, INV 5to5 (in turn) whose breakpoints lie `span` apart, reported with sv_end - sv_start = span - 1,
+    span, span + 1 (in turn, every fourth junction): with indelsize = min_cons_window = span every junction sits on one of
+    the comparisons `svEnd - svStart <= indelsize` / `> minConsWindow` (src/split.h:116,124,139,158,606).  Consensus: the ALT
+    haplotype around the junction, flanks of 40 .. 140 bases (lr: 700 .. 1150, 1 % substitutions, sparse 1-base indels,
+    every third one reverse-complemented); flank = f: flanks f and f - 1 / f / f + 1 (in turn), i.e. |consensus| =
+    2 f - 1, 2 f, 2 f + 1 -- the comparison `consensus.size() < 2 * minimumFlankSize + insLen` (src/split.h:647) at
+    minimumFlankSize = f."""
+    W = synth.WINDOW_LR if lr else synth.WINDOW
+    s = 6000 if lr else 1500
+    chrom = np.empty(n * W, dtype=np.uint8)
+    junc = np.zeros(n, dtype=abi.junction_dtype())
+    seqs = []
+    for k in range(n):
+        rng = synth._rng(seed, k)
+        G = synth.ACGT[rng.integers(0, 4, W)]
+        svt, kind = _SV_KINDS[k % 4]
+        e = s + span
+        if flank is None:
+            fl, fr = (int(rng.integers(700, 1150)), int(rng.integers(700, 1150))) if lr else (int(rng.integers(40, 140)), int(rng.integers(40, 140)))
+        else:
+            fl, fr = flank, flank + (k // 4) % 3 - 1
+        L = max(fl, fr)
+        if kind == "del":
+            left, right = G[s - L:s], G[e:e + L]
+        elif kind == "dup":
+            left, right = G[e - L:e], G[s:s + L]
+        elif kind == "inv0":
+            left, right = G[s - L:s], synth.revcomp(G[e - L:e])
+        else:
+            left, right = synth.revcomp(G[s:s + L]), G[e:e + L]
+        cons = synth._mutate(rng, np.concatenate([left[L - fl:], right[:fr]]), 0.01 if lr else 0.005)
+        if lr and flank is None:
+            keep = rng.random(cons.size) >= 0.004
+            cons = cons[keep]
+            at = np.nonzero(rng.random(cons.size) < 0.004)[0]
+            cons = np.insert(cons, at, synth.ACGT[rng.integers(0, 4, at.size)])
+        if lr and k % 3 == 2:
+            cons = synth.revcomp(cons)
+        chrom[k * W:(k + 1) * W] = G
+        junc[k]["svid"] = k
+        junc[k]["svt"] = svt
+        junc[k]["sv_start"] = k * W + s
+        junc[k]["sv_end"] = k * W + s + span + (k // 4) % 3 - 1 if flank is None else k * W + e
+        junc[k]["seq_first"] = k
+        junc[k]["n_seq"] = 1
+        seqs.append(cons)
+    return _pack([chrom], junc, seqs)
+
+
+def ins_at_flank(n, mfs, *, seed=2, lr=False, buffer=False):
+    """svt 4 junctions whose consensus (left flank + insertion I + right flank) sits on an alignConsensus threshold at
+    minimumFlankSize = mfs, the reported ins_len chosen per junction (it is an estimate, src/split.h:647,652):
+      buffer=False: flanks mfs + 10 each, ins_len = I + 20 + (-1, 0, +1 in turn) -> |consensus| = 2 mfs + ins_len - d,
+                    i.e. `consensus.size() < 2 * minimumFlankSize + insLen` at -1 / 0 / +1;
+      buffer=True : the same consensus, ins_len = I + 20 - mfs - d for d = -1 .. 3 -> (|consensus| - insLen) / 3 crosses
+                    minimumFlankSize in `bufferSpace = max((consensus.size() - insLen) / 3, minimumFlankSize)`.
+    I: mfs + 5 .. mfs + 80 bases (lr: 600 .. 900)."""
+    W = synth.WINDOW_LR if lr else synth.WINDOW
+    s = 6000 if lr else 1500
+    chrom = np.empty(n * W, dtype=np.uint8)
+    junc = np.zeros(n, dtype=abi.junction_dtype())
+    seqs = []
+    for k in range(n):
+        rng = synth._rng(seed, k)
+        G = synth.ACGT[rng.integers(0, 4, W)]
+        I = int(rng.integers(600, 901)) if lr else int(rng.integers(mfs + 5, mfs + 81))
+        f = mfs + 10
+        cons = synth._mutate(rng, np.concatenate([G[s - f:s], synth.ACGT[rng.integers(0, 4, I)], G[s:s + f]]), 0.01 if lr else 0.005)
+        d = (k % 5) - 1 if buffer else (k % 3) - 1
+        chrom[k * W:(k + 1) * W] = G
+        junc[k]["svid"] = k
+        junc[k]["svt"] = 4
+        junc[k]["sv_start"] = k * W + s
+        junc[k]["sv_end"] = k * W + s + int(rng.integers(0, 3))
+        junc[k]["ins_len"] = I + 20 - mfs - d if buffer else I + 20 + d
+        junc[k]["seq_first"] = k
+        junc[k]["n_seq"] = 1
+        seqs.append(cons)
+    return _pack([chrom], junc, seqs)
+
+
+def flank_slack(res):
+    """per record of an accepted junction: the largest minimumFlankSize its flank tests (src/split.h:370-371) still pass
+    -- min(cStart - homLeft, |consensus| - cEnd - homRight, rStart - homLeft, |svRefStr| - rEnd - homRight); -1 elsewhere"""
+    s = np.minimum.reduce([res["c_start"] - res["hom_left"], res["cons_len"] - res["c_end"] - res["hom_right"],
+                           res["r_start"] - res["hom_left"], res["ref_len"] - res["r_end"] - res["hom_right"]])
+    return np.where(res["ok"] != 0, s, -1)

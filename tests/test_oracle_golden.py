@@ -279,3 +279,39 @@ def test_c_restatement_under_address_and_undefined_behaviour_sanitizers():
         pytest.skip("no sanitizer runtime in this toolchain")
     assert r.returncode == 0, r.stdout[-3000:]
     assert "sanitize_selftest: done rc=0" in r.stdout
+
+
+LR_OPTIONS = [("minimum_flank_size", 30), ("minimum_flank_size", 250), ("flank_quality", 0.97), ("indelsize", 500),
+              ("indelsize", 30000), ("min_cons_window", 300), ("min_cons_window", 3000)]
+
+
+def _with(p, **kw):
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def test_port_vs_reference_under_delly_options(port, reference):
+    """the restatement at the non-default `delly lr` options and on the threshold batches of tests/test_gpu_options.py:
+    one option changed at a time on long-read consensus / msaWfa batches, spans on indelsize = minConsWindow, consensus
+    lengths on 2 * minimumFlankSize (+ insLen), bufferSpace around minimumFlankSize, and -z on the short-read MSA"""
+    import fuzz
+    runs = []
+    lr, lrins = synth.make_batch(6, seed=301, mode="lr", sub_rate=0.01), synth.make_batch(3, seed=305, mode="lrins", n_reads=4, sub_rate=0.04)
+    for k, v in LR_OPTIONS:
+        runs.append(("lr %s=%s" % (k, v), lr, _with(abi.params_lr(realign=True), **{k: v})))
+    runs.append(("lrins -w 3000", lrins, _with(abi.params_lr(realign=True), min_cons_window=3000)))
+    for span in (400, 1000):
+        runs.append(("sr span %d" % span, fuzz.at_span(48, span, seed=span), _with(abi.params_sr(), indelsize=span, min_cons_window=span)))
+    runs.append(("lr span 3000", fuzz.at_span(8, 3000, seed=3000, lr=True), _with(abi.params_lr(realign=True), indelsize=3000, min_cons_window=3000)))
+    runs.append(("sr |consensus| 2 * 40", fuzz.at_span(24, 500, seed=40, flank=40), _with(abi.params_sr(), minimum_flank_size=40)))
+    runs.append(("lr |consensus| 2 * 500", fuzz.at_span(12, 2000, seed=500, lr=True, flank=500), _with(abi.params_lr(realign=True), minimum_flank_size=500)))
+    for buffer in (False, True):
+        runs.append(("sr ins buffer=%d" % buffer, fuzz.ins_at_flank(30, 40, seed=40 + buffer, buffer=buffer), _with(abi.params_sr(), minimum_flank_size=40)))
+        runs.append(("lr ins buffer=%d" % buffer, fuzz.ins_at_flank(10, 300, seed=300 + buffer, lr=True, buffer=buffer), _with(abi.params_lr(realign=True), minimum_flank_size=300)))
+    for z in (3, 5, 20):
+        runs.append(("sr msa -z %d" % z, synth.make_batch(24, mode="c2", seed=311, n_reads=(2, 20), sub_rate=0.02), _with(abi.params_sr(), min_clique_size=z)))
+    for label, b, p in runs:
+        rr, rb = reference.refine_batch(b, params=p, n_threads=8)
+        pr, pb = port.refine_batch(b, params=p, n_threads=8)
+        compare(pr, pb, rr, rb, label=label)
