@@ -315,3 +315,47 @@ def test_port_vs_reference_under_delly_options(port, reference):
         rr, rb = reference.refine_batch(b, params=p, n_threads=8)
         pr, pb = port.refine_batch(b, params=p, n_threads=8)
         compare(pr, pb, rr, rb, label=label)
+
+
+def _route_batches():
+    """every batch of tests/test_gpu_routes.py but the large scratch-growth one, with the parameters it runs under"""
+    import route_edges as R
+    wide = _with(abi.params_sr(), indelsize=R.WIDE_INDELSIZE)
+    out = [("grid " + k, b, p) for k, (b, p) in sorted(R.grid_batches().items())]
+    out.append(("counters", R.counter_batch(), wide))
+    out.append(("deferral", R.deferral_batch(), abi.params_sr()))
+    out += [("seats %d/%d" % qp, R.seat_batch(*qp), wide) for qp in ((5, 3), (6, 5), (7, 7))]
+    out.append(("wide kernel", R.wide_kernel_batch(40, seed=43), wide))
+    return out
+
+
+def test_route_edge_generator_hits_its_shapes(port):
+    """tests/route_edges.py: the C restatement reports exactly the consensus length and window length |svRefStr| each junction
+    was built for (a change to the generator or to synth.py cannot quietly move the kernel-routing edges), the grid covers
+    every (m, n) asked for and the corners of the byte tile, and the wide-alphabet consensus holds its number of distinct bytes"""
+    import route_edges as R
+    for label, b, p in _route_batches():
+        res, _ = port.refine_batch(b, params=p, want_alignment=False, n_threads=8)
+        m = np.array([t["m"] for t in b.truth])
+        n = np.array([t["n"] for t in b.truth])
+        assert (res["cons_len"] == m).all(), label
+        assert (res["ref_len"] == n).all(), (label, np.nonzero(res["ref_len"] != n)[0][:5])
+        for k, t in enumerate(b.truth):
+            if t["distinct"] is not None:
+                assert len(set(b.seqs_of(k)[0])) == t["distinct"], (label, k)
+    cells = {(t["m"], t["n"], t["kind"]) for b, _ in R.grid_batches().values() for t in b.truth}
+    for m in R.GRID_M:
+        assert all((m, n, "del") in cells for n in R.GRID_N), m
+        assert all((m, 4 * m, k) in cells for k in R.TWO_WINDOW_KINDS), m
+    assert all((m, n, "del") in cells for m, n in R.CORNERS)
+    deferral = R.deferral_batch()
+    assert {t["distinct"] for t in deferral.truth} == set(R.DEFER_D) | {None}
+    assert max(t["distinct"] or 0 for t in deferral.truth) - 4 <= len(R.EXTRA)
+
+
+def test_port_vs_reference_on_route_edges(port, reference):
+    """the restatement against the reference on every route-edge batch: the GPU tests read the INTERNAL fields from it"""
+    for label, b, p in _route_batches():
+        rr, rb = reference.refine_batch(b, params=p, n_threads=8)
+        pr, pb = port.refine_batch(b, params=p, n_threads=8)
+        compare(pr, pb, rr, rb, label=label)
